@@ -10,8 +10,14 @@ decode shape: drop-in on the HIP kernels vs the CPU hook path), --config 2 (deco
 --config 4 (Qwen2-7B, TriviaQA, ideal scores, all heads, decode),
 --config 5 (Llama-3-8B, 20 retrieved docs ~8k tokens, decode).
 
-Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
       (N > 1 under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`)
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the result line
+(config 3: the IE sweep alone; configs 1, 2, 4, 5: the decode alone).  --full adds everything else the line can
+carry: config 3's decode leg (config 2's workload, `decode`), the decode attention kernel's roofline launches and the
+CPU baselines (`cpu_baseline`, `speedup_vs_cpu`).  --dump-outputs DIR writes what the last timed step returned to its
+caller as DIR/<name>.npy (config 3: `ie`, the IE grids [questions of the step, L, H]; decode: `decode_answers`, the
+generated ids [questions, new tokens]); the inputs are the same from run to run, so two builds compare output for output.
 Weights are random-init of the named architecture (no checkpoint offline);
 prompts are the rebuilt NQ/TriviaQA-1000 inputs through the offline BPE tokenizers
 with the model family's chat template (mean ~962 tokens with the wrong answer appended).
@@ -136,6 +142,25 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT = 64 * 10**6       # bytes of --dump-outputs in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: every array of {name: ndarray} as path/<name>.npy, float32 (float64 arrays stay float64).  The
+    files hold at most `limit` bytes in all: a larger set is cut to a fixed sample, the same elements of every array's
+    flattened values in every run (numpy default_rng(0), sorted indices), each array keeping its share of the bytes."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes + 128 for a in arrays.values())          # + the .npy header
+    for name, a in arrays.items():
+        if total > limit:
+            keep = max(1, int(a.size * limit / total) - 128 // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def load_dataset(name):
     with gzip.open(os.path.join(REPO, "data", f"{name}_1000.json.gz"), "rt", encoding="utf-8") as f:
         return json.load(f)
@@ -165,6 +190,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=3, choices=[1, 2, 3, 4, 5])
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: config 3's decode leg, the decode attention "
+                         "kernel's roofline launches, the CPU baselines (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     # max rows per decode batch.  Round 6: NQ-1000 on one GPU in ONE batch of 1000 rows (KV cache ~180 GB of the 288
     # GB: --kv-frac 0.68): every decode step's 15 GB weight read and its projections serve all 1000 rows, 34.2 ms per
     # step against 2 x 18.8 for two batches of 500 -- 81.8 vs 79.5 questions/s on one box (profiles/r06/decode_b*.json;
@@ -200,6 +230,12 @@ def main():
     ap.add_argument("--expandable-segments", action="store_true",
                     help="PYTORCH_HIP_ALLOC_CONF=expandable_segments:True (A/B of the caching allocator's segments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: the headline figure's workload only (config 3: the sweep; the others: the decode)
+        args.no_cpu_baseline = True
+        args.no_decode = args.no_decode or args.config == 3
     if args.expandable_segments:
         os.environ["PYTORCH_HIP_ALLOC_CONF"] = "expandable_segments:True"      # before torch initialises HIP
 
@@ -332,7 +368,8 @@ def main():
         assert tuple(full.shape) == (n_t, L, H) and torch.isfinite(full).all(), "non-finite or missing IE"
         ie = {"value": units / elapsed, "elapsed": elapsed, "flops": flops_all, "flops_executed": flops_ex_all,
               "base_variant": base_variant, "kt": kt, "kg": kg, "kc": kc,
-              "mean_T": sum(x[1].numel() for x in work) / len(work), "work": work}
+              "mean_T": sum(x[1].numel() for x in work) / len(work), "work": work,
+              "last_step": full[-world * len(positions):]}      # the IE grids of the last timed step's questions
         log(f"[rank {rank}] IE sweep: {units} units in {elapsed:.2f}s -> {ie['value']:.1f} heads/s")
 
     # ------------------------------------------------------------------ batched reweighted decode (configs 2, 4, 5)
@@ -340,7 +377,7 @@ def main():
     # each rank's share in batches of at most --decode-batch rows, answers all-gathered), as RAG_test.py:64-176 answers
     # every question once: NQ-1000 / TriviaQA-1000 for configs 2-4 (strong scaling over N), config 5 one KV-budget
     # batch per GPU of long-context questions.
-    decode = None
+    decode = answers = None
     dec_cpu_input = None
     if not args.no_decode:
         if model == "qwen2-7b":
@@ -435,7 +472,7 @@ def main():
                            "(random weights)")}
         if phases:
             decode["leg_roofline"] = decode_leg_roofline(spec, phases, mdtype)
-        if my_batches:
+        if my_batches and args.full:
             b0 = my_batches[0]
             decode["attention_roofline"] = decode_attention_roofline(eng, [dev_prompts[i] for i in b0],
                                                                      [ws[i] for i in b0], heads, args.decode_tokens,
@@ -641,6 +678,14 @@ def main():
                            "roofline": decode.get("attention_roofline"), "cpu_baseline": cpu_dec, "decode": decode})
             if cpu_dec:
                 result["speedup_vs_cpu"] = decode["speedup_vs_cpu"]
+        if args.dump_outputs:
+            import numpy as np
+            arrays = {}
+            if ie is not None:
+                arrays["ie"] = ie["last_step"].float().cpu().numpy()
+            if answers is not None:                 # token ids (< 2^24: exact in float32), the last repeat's
+                arrays["decode_answers"] = np.asarray(answers, dtype=np.float32)
+            dump_outputs(args.dump_outputs, arrays)
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.barrier()
@@ -692,9 +737,13 @@ def run_config1(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(max(1, args.steps)):
-        run_gpu()
+        outs = run_gpu()
     torch.cuda.synchronize()
     gpu_s = (time.perf_counter() - t0) / max(1, args.steps)
+    if args.dump_outputs:
+        import numpy as np
+        new = [o[0, ids.shape[1]:].tolist() for o, (ids, _) in zip(outs, prompts)]     # the 32 generated ids per question
+        dump_outputs(args.dump_outputs, {"decode_answers": np.asarray(new, dtype=np.float32)})
     value = len(prompts) / gpu_s
     log(f"[config 1] GPU drop-in: {value:.2f} questions/s ({gpu_s:.2f} s for 8 questions)")
     cpu = None

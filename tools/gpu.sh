@@ -8,7 +8,7 @@
 #   suite            pytest -m gpu (every GPU test, -x)
 #   suite-all        pytest -m gpu without -x (every failure listed)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (config 3 + decode, CPU baselines)
+#   bench            the whole bench line (bench.py --full: config 3 + decode, CPU baselines)
 #   bench:ARGS       bench.py with ARGS (commas become spaces), e.g. bench:--config,2,--no-cpu-baseline
 #   benv:ENV:ARGS    bench.py ARGS under ENV (NAME=V pairs joined by +), e.g. benv:CRAM_FUSED_QKV=0:--no-decode (A/B arms)
 #   prof             rocprofv3 --kernel-trace --stats of the sweep-only bench (summary kept, traces deleted)
@@ -35,7 +35,7 @@ for step in "$@"; do
     suite-all) timeout -k 10 1000 $PYT -v > $O/gputest.txt 2>&1 || echo "pytest rc=$?"; tail -5 $O/gputest.txt ;;
     smoke)     timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
                tail -2 $O/smoke.txt ;;
-    bench)     timeout -k 10 560 python -u bench.py > $O/bench.json 2> $O/bench.err; head -c 700 $O/bench.json; echo ;;
+    bench)     timeout -k 10 560 python -u bench.py --full > $O/bench.json 2> $O/bench.err; head -c 700 $O/bench.json; echo ;;
     bench:*)   a=${step#bench:}; n=$(echo "$a" | tr -c 'a-zA-Z0-9' '_' | cut -c1-60)
                timeout -k 10 900 python -u bench.py ${a//,/ } > $O/bench_$n.json 2> $O/bench_$n.err
                head -c 700 $O/bench_$n.json; echo ;;
